@@ -25,6 +25,11 @@ The same line carries:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run times the headline alone: set-up, warm-up, the K timed steps and the line.  Everything else above -- the
+side chains, the comparison with the CPU reference, the host-fed and drop-in legs, rx_power, the channeliser, sdr_convert,
+the CPU baselines, the box ceilings and the full record -- runs with --full.  --dump-outputs DIR writes what the last
+timed step computed as DIR/*.npy (float32/float64), so that two builds can be compared output for output.
+
 rx_fm does not shard (one stream, sequential carries): N>1 runs N independent replicas
 ("replicas only", weak scaling).  rx_power shards by tune (strong scaling of one sweep).
 torch is used for device buffers, the synthetic capture and torch.distributed's rendezvous only; every sample is
@@ -297,6 +302,27 @@ def device_capture(torch, dev, n_complex, seed, fs=20.06e6, amp=20000.0, tone=10
     return out
 
 
+DUMP_MAX_SAMPLES = 12 << 20    # 48 MiB of float32: the outputs of one dump stay under 64 MB
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_fm_outputs(out_dir, d_out, n, carry):
+    """--dump-outputs: what a caller of the timed rxgpu_fm_stream_run_async gets from the last step -- the n int16 of d_out and the carries the
+    wait brought back.  fm_audio.npy: the samples as float32, all of them up to DUMP_MAX_SAMPLES, else that many at indices drawn without
+    replacement by numpy's default_rng(DUMP_SAMPLE_SEED) from range(n), in index order; fm_out_len.npy: [n]; fm_carry.npy: every field of
+    struct rxgpu_fm_carry in declaration order, arrays flattened (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    audio = d_out[:n].cpu().numpy()
+    if n > DUMP_MAX_SAMPLES:
+        audio = audio[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_MAX_SAMPLES, replace=False))]
+    fields = []
+    for name, _ in carry._fields_:
+        fields.extend(np.ctypeslib.as_array(getattr(carry, name)).ravel().tolist() if hasattr(getattr(carry, name), "_length_") else [getattr(carry, name)])
+    np.save(os.path.join(out_dir, "fm_audio.npy"), audio.astype(np.float32))
+    np.save(os.path.join(out_dir, "fm_out_len.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "fm_carry.npy"), np.array(fields, dtype=np.float64))
+
+
 def parity_module():
     """tests/parity_at_size.py: the checks against the CPU reference at bench size (checker infrastructure, loads oracle/)"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -508,8 +534,13 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=80.0, help="untimed milliseconds of the same step in front of the warm-up steps (0: none)")
     ap.add_argument("--blocks", type=int, default=16384, help="rx_fm blocks of 131072 complex samples per step (16384 = 8 GiB of cs16)")
     ap.add_argument("--passes", type=int, default=512, help="rx_power scanner() passes per step (one report interval)")
-    ap.add_argument("--workload", default="both", choices=["both", "rx_fm", "rx_power", "chan", "sdr"])
-    ap.add_argument("--cpu-seconds", type=float, default=9.0, help="CPU baseline budget per path (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: side chains, parity at bench size, host-fed and drop-in legs, the other workloads, "
+                         "CPU baselines, box ceilings, the full record (a plain run times the rx_fm headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (output samples, their count, the carries) as DIR/*.npy")
+    ap.add_argument("--workload", default=None, choices=["both", "rx_fm", "rx_power", "chan", "sdr"], help="with --full (default both); a plain run is rx_fm")
+    ap.add_argument("--cpu-seconds", type=float, default=9.0, help="with --full: CPU baseline budget per path (0 = skip)")
     ap.add_argument("--prof-level", type=int, default=1)
     ap.add_argument("--cpu-worker", default=None, choices=["fm", "power"], help=argparse.SUPPRESS)
     ap.add_argument("--cpu-lib", default="", help=argparse.SUPPRESS)
@@ -527,6 +558,15 @@ def main():
     if args.cpu_worker:
         cpu_worker(args.cpu_worker, args.cpu_seconds, args.cpu_lib)
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.workload is None:
+        args.workload = "both" if args.full else "rx_fm"
+    elif args.workload != "rx_fm" and not args.full:
+        ap.error("--workload %s needs --full (a plain run times the rx_fm headline only)" % args.workload)
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line -- no side figure, no check, no baseline
+        args.variants, args.no_parity, args.cpu_seconds = "none", True, 0.0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
@@ -605,9 +645,11 @@ def main():
         g = C.c_double(0)
         R.check(L.rxgpu_diag_stream_rate(mode, units, reps, C.byref(g)))
         return g.value
-    box = {"read_only_GBs": box_rate(0), "copy_1_1_GBs": box_rate(1), "expand_1_2_GBs": box_rate(2, 1 << 27), "shrink_2_1_GBs": box_rate(3),
-           "read_only_grid_stride_loop_GBs": box_rate(4),
-           "how": "rxgpu_diag_stream_rate: 1 GiB read per launch, 5 launches, hipEvents; read + written bytes"}
+    box = None
+    if args.full:
+        box = {"read_only_GBs": box_rate(0), "copy_1_1_GBs": box_rate(1), "expand_1_2_GBs": box_rate(2, 1 << 27), "shrink_2_1_GBs": box_rate(3),
+               "read_only_grid_stride_loop_GBs": box_rate(4),
+               "how": "rxgpu_diag_stream_rate: 1 GiB read per launch, 5 launches, hipEvents; read + written bytes"}
 
     # ------------------------------------------------------------------ rx_fm (headline)
     if args.workload in ("both", "rx_fm"):
@@ -619,6 +661,7 @@ def main():
         d_out = torch.zeros(T // 118 + 64, dtype=torch.int16, device=dev)
         hp = dict(downsample=118)
         s = R.FmStream(R.FmParams.wbfm(**hp), n_blocks, block_len)
+        carry0 = s.get_carry()
         # Untimed, in front of the W warm-up steps: --settle-ms of the same step.  The first ~50 ms of this loop after the device has done other work
         # (the box probes, the capture generator) run 2-3 % slower than its steady state -- twelve alternating runs on one box: 0.790-0.817 of HBM
         # without, 0.805-0.832 with 60 ms of it, 0.831-0.833 with --warmup 50 (profiles/r06_settle_ab.txt); a read-only probe of the same length does
@@ -627,6 +670,9 @@ def main():
         while (time.perf_counter() - t_s) * 1e3 < args.settle_ms:
             s.run_async(d_iq.data_ptr(), n_blocks, block_len, d_out.data_ptr(), d_out.numel())
             s.wait()
+        # the settle loop runs for a time, not a count: back to the fresh stream's carries, so that the W + K runs behind this (and the last
+        # step's output, --dump-outputs) are the same from run to run
+        s.set_carry(carry0)
         for _ in range(args.warmup):
             s.run_async(d_iq.data_ptr(), n_blocks, block_len, d_out.data_ptr(), d_out.numel())
         s.wait()
@@ -636,13 +682,15 @@ def main():
         t0 = time.perf_counter()
         # pipelined: run r+1's decimator (stream A) overlaps run r's audio stages (stream B); one wait at the end
         for _ in range(args.steps):
-            s.run_async(d_iq.data_ptr(), n_blocks, block_len, d_out.data_ptr(), d_out.numel())
+            n_last, _ = s.run_async(d_iq.data_ptr(), n_blocks, block_len, d_out.data_ptr(), d_out.numel())
         s.wait()
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         L.rxgpu_prof_enable(0)
         ms, launches = prof("fm_decimate")
         fixups = s.host_fixups
+        if args.dump_outputs and rank == 0:
+            dump_fm_outputs(args.dump_outputs, d_out, n_last, s.get_carry())
         s.close()
         del d_out
         parity = {}
@@ -840,9 +888,10 @@ def main():
             "host_fed": host_fed,
             "roofline": {"bound": "hbm", "kernel": "k_fm_decimate (F0+F1+F2)", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "box_ceilings": box, "frac_of_box_read_only": achieved / box["read_only_GBs"],
                          "algorithmic_bytes_per_launch": 4 * T, "avg_launch_ms": (ms / launches) if launches else None},
         })
+        if box is not None:
+            result["roofline"].update({"box_ceilings": box, "frac_of_box_read_only": achieved / box["read_only_GBs"]})
         result.update(parity)
         if parity:
             parity_all["rx_fm"] = bool(parity["parity_ok"])
@@ -1447,16 +1496,17 @@ def main():
         if parity_all:
             result["parity_all_legs"] = parity_all
             result["parity_ok"] = all(parity_all.values())
-        full = json.dumps(result)
         full_path = None
-        try:
-            os.makedirs(os.path.dirname(args.full_out), exist_ok=True)
-            with open(args.full_out, "w") as f:
-                f.write(full + "\n")
-            full_path = os.path.relpath(args.full_out, ROOT) if os.path.abspath(args.full_out).startswith(ROOT + os.sep) else os.path.abspath(args.full_out)
-        except OSError as e:
-            sys.stderr.write("bench.py: full record not written to %s: %s\n" % (args.full_out, e))
-        sys.stderr.write("BENCH_FULL " + full + "\n")
+        if args.full:
+            full = json.dumps(result)
+            try:
+                os.makedirs(os.path.dirname(args.full_out), exist_ok=True)
+                with open(args.full_out, "w") as f:
+                    f.write(full + "\n")
+                full_path = os.path.relpath(args.full_out, ROOT) if os.path.abspath(args.full_out).startswith(ROOT + os.sep) else os.path.abspath(args.full_out)
+            except OSError as e:
+                sys.stderr.write("bench.py: full record not written to %s: %s\n" % (args.full_out, e))
+            sys.stderr.write("BENCH_FULL " + full + "\n")
         sys.stderr.flush()
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)

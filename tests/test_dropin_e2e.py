@@ -71,6 +71,15 @@ def dropin_bin(name, patched=False):
     return os.path.join(ROOT, "oracle", "_ref", "dropin_bin_patched" if patched else "dropin_bin", name)
 
 
+def dropin_env(**kw):
+    """The executables' environment: this tree's librxgpu.so ahead of the run path baked in at link time, which points wherever the binaries
+    were linked -- a tree the binaries were copied or linked into from elsewhere must still run them against its own library"""
+    lib_dir = os.path.join(ROOT, "rx_tools_amd")
+    assert os.path.exists(os.path.join(lib_dir, "librxgpu.so")), "librxgpu.so not built (make -C rx_tools_amd/csrc)"
+    ld = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib_dir + (os.pathsep + ld if ld else ""), **kw)
+
+
 def run_dropin_rx_fm(iq, tmp_path, extra, patched):
     """the product's rx_fm executable on a capture file, replayed at a quarter of real time (the reference's hand-off between its
     dongle and demod threads is a single lossy slot, rtl_fm.c:858-862/921-924: a real-time source never overruns it), ^C at the end"""
@@ -79,7 +88,7 @@ def run_dropin_rx_fm(iq, tmp_path, extra, patched):
         pytest.skip("dropin binaries not built (make -C oracle ref)")
     iq_path, out_path = str(tmp_path / "iq.cs16"), str(tmp_path / "out.raw")
     iq.tofile(iq_path)
-    env = dict(os.environ, SOAPY_FAKE_FILE=iq_path, SOAPY_FAKE_PACE="0.25", SOAPY_FAKE_EOF_SIGINT="300")
+    env = dropin_env(SOAPY_FAKE_FILE=iq_path, SOAPY_FAKE_PACE="0.25", SOAPY_FAKE_EOF_SIGINT="300")
     p = subprocess.run([exe] + extra + [out_path], env=env, capture_output=True, timeout=300)
     assert os.path.exists(out_path), p.stderr.decode()[-2000:]
     return np.fromfile(out_path, dtype=np.int16), p.stderr.decode()
@@ -190,7 +199,7 @@ def run_dropin_rx_power(data, plan, tmp_path, extra):
     np.ascontiguousarray(data).tofile(iq_path)
     # scanner() asks for buf_len ELEMENTS but consumes buf_len int16 (rtl_power.c:526/715): the device hands out buf_len/2 per read;
     # retune()'s flush reads go to the file-static `dump`, which the unit tells the replay device to leave the capture alone for
-    env = dict(os.environ, SOAPY_FAKE_FILE=iq_path, SOAPY_FAKE_MAX_READ=str(plan.buf_len // 2))
+    env = dropin_env(SOAPY_FAKE_FILE=iq_path, SOAPY_FAKE_MAX_READ=str(plan.buf_len // 2))
     p = subprocess.run([exe] + extra + [out_path], env=env, capture_output=True, timeout=300)
     assert os.path.exists(out_path), p.stderr.decode()[-2000:]
     return [line.split(", ", 2)[2] for line in open(out_path).read().splitlines()], p.stderr.decode()

@@ -194,7 +194,7 @@ def test_bench_multi_rank_path_on_one_gpu(world, form, tmp_path):
         env.pop(k, None)
     full_path = str(tmp_path / "full.json")
     # (--settle-ms 10: two untimed steps of the sharded sweep in front of the warm-up, each with its gather)
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--settle-ms", "10", "--blocks", "256", "--passes", "8", "--cpu-seconds", "1.5", "--full-out", full_path]
+    args = ["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--settle-ms", "10", "--blocks", "256", "--passes", "8", "--cpu-seconds", "1.5", "--full-out", full_path]
     if form == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(root, "bench.py")] + args

@@ -228,6 +228,50 @@ def test_bench_compact_line_stays_small_and_strict():
     assert len(line) < bench.COMPACT_LIMIT and "legs" not in json.loads(line)["roofline"]
 
 
+def test_bench_dump_outputs_are_float_small_and_seeded(tmp_path):
+    """--dump-outputs: the last step's samples as float32 (a seeded sample of DUMP_MAX_SAMPLES above that), its length and every carry field as
+    float64; the same arguments give the same files, and the whole dump stays under 64 MB at the bench's default size"""
+    import os, sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from rx_tools_amd.fm import FmCarry
+    assert bench.DUMP_MAX_SAMPLES * 4 + 8 * 200 < 64e6
+    c = FmCarry()
+    c.prev_index, c.lp_q_hist[9][5], c.dc_avgQ = 17, -3, 5
+    out = torch.arange(-500, 500, dtype=torch.int16)
+    files = {}
+    for run, limit in (("a", 600), ("b", 600), ("all", 10 ** 6)):
+        bench.DUMP_MAX_SAMPLES, keep = limit, bench.DUMP_MAX_SAMPLES
+        try:
+            bench.dump_fm_outputs(str(tmp_path / run), out, 900, c)
+        finally:
+            bench.DUMP_MAX_SAMPLES = keep
+        files[run] = {f: np.load(str(tmp_path / run / f)) for f in sorted(os.listdir(str(tmp_path / run)))}
+    assert sorted(files["a"]) == ["fm_audio.npy", "fm_carry.npy", "fm_out_len.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for r in files.values() for v in r.values())
+    assert all(np.array_equal(files["a"][f], files["b"][f]) for f in files["a"])
+    assert np.array_equal(files["all"]["fm_audio.npy"], np.arange(-500, 400, dtype=np.float32))
+    a = files["a"]["fm_audio.npy"]
+    assert a.size == 600 and np.all(np.diff(a) > 0) and set(a.tolist()) <= set(range(-500, 400))
+    assert files["a"]["fm_out_len.npy"].tolist() == [900.0]
+    k = files["a"]["fm_carry.npy"]
+    assert k.size == 5 + 2 * 60 + 2 * 9 + 7 and k[2] == 17 and k[5 + 60 + 59] == -3 and k[-1] == 5
+
+
+def test_bench_plain_run_refuses_what_needs_full():
+    """a plain run times the rx_fm headline alone: another workload asks for --full instead of being dropped unnoticed"""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for wl in ("both", "rx_power", "chan", "sdr"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", wl], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        assert out.returncode == 2 and b"needs --full" in out.stderr and not out.stdout
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert out.returncode == 2 and b"--steps" in out.stderr
+
+
 def test_bench_self_launches_when_gpus_gt_1_without_torchrun(tmp_path):
     """`python bench.py --gpus N` (the shape of the driver's N=1 command) must not die on launch shape at N > 1: without WORLD_SIZE it re-executes
     itself under torch.distributed.run with one process per GPU.  Checked here by pointing the re-exec at a stand-in interpreter that records its argv."""

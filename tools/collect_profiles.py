@@ -137,7 +137,7 @@ def main():
                         "tools/chain_once.py 8192 %d 2: two pipelined runs of 8192 blocks (4 GiB each); counters summed over every kernel of the chain, per run" % ds)
         if e:
             chains[label] = e
-    e = chain_entry(src, "rx_power", 3, 4.0 * 512 * 599 * 8192, "bench.py --workload rx_power --steps 2 --warmup 1: three 512-pass launches of the configs[2] geometry")
+    e = chain_entry(src, "rx_power", 3, 4.0 * 512 * 599 * 8192, "bench.py --full --workload rx_power --steps 2 --warmup 1: three 512-pass launches of the configs[2] geometry")
     if e:
         chains["rx_power configs[2]"] = e
     e = chain_entry(src, "chan", 6, 4.0 * 2048 * 131072, "tools/chan_once.py: six runs of the bench shape, 1 GiB of capture each")

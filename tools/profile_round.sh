@@ -33,13 +33,13 @@ pmc() { # DIR-PREFIX "counter sets..." -- CMD...   one rocprofv3 --pmc run per s
   done
 }
 if has bench; then
-  python $REPO/bench.py --steps 20 --warmup 5 --full-out $OUT/bench_full.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+  python $REPO/bench.py --full --steps 20 --warmup 5 --full-out $OUT/bench_full.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err
   echo "bench rc=$? stdout $(wc -l < $OUT/bench_n1.json) line(s) $(wc -c < $OUT/bench_n1.json) bytes"
 fi
 if has trace; then
   rm -rf $OUT/trace $OUT/trace_variants
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $REPO/bench.py --steps 20 --warmup 5 --variants none --no-parity --full-out $OUT/trace_bench_full.json > $OUT/trace_bench.json 2> $OUT/trace.log
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_variants -- python $REPO/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --workload rx_fm --no-parity --full-out $OUT/trace_variants_full.json > $OUT/trace_variants.json 2> $OUT/trace_variants.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $REPO/bench.py --full --steps 20 --warmup 5 --variants none --no-parity --full-out $OUT/trace_bench_full.json > $OUT/trace_bench.json 2> $OUT/trace.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_variants -- python $REPO/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --workload rx_fm --no-parity --full-out $OUT/trace_variants_full.json > $OUT/trace_variants.json 2> $OUT/trace_variants.log
 fi
 if has chains; then
   for ds in 118 6 5 -7 -39; do
@@ -47,7 +47,7 @@ if has chains; then
   done
 fi
 if has power; then
-  pmc rx_power "$SQ|FETCH_SIZE|WRITE_SIZE|$LDS" python $REPO/bench.py --steps 2 --warmup 1 --settle-ms 0 --cpu-seconds 0 --workload rx_power --variants none --no-parity --full-out $OUT/pmc_power_full.json
+  pmc rx_power "$SQ|FETCH_SIZE|WRITE_SIZE|$LDS" python $REPO/bench.py --full --steps 2 --warmup 1 --settle-ms 0 --cpu-seconds 0 --workload rx_power --variants none --no-parity --full-out $OUT/pmc_power_full.json
 fi
 if has chan; then
   pmc chan "$SQ|FETCH_SIZE|WRITE_SIZE|$LDS" python $REPO/tools/chan_once.py
