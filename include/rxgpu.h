@@ -262,7 +262,20 @@ long rxgpu_fm_stream_host_fixups(const rxgpu_fm_stream *s);
  * Channel response: a rectangular N-sample window, critically sampled -- each channel is the boxcar low_pass of the reference, so its
  * selectivity is a sinc's (first side lobe -13 dB, nulls at the neighbouring channel centres): adjacent-channel energy away from those
  * centres leaks in, exactly as it does into rx_fm's own low_pass at ds = N.  There is no windowed / polyphase prototype filter here,
- * because the reference has none to pin one against. */
+ * because the reference has none to pin one against.
+ *
+ * Demodulators and squelch (mode .. squelch_zero; all zero = FM without squelch, as before).  Every channel runs full_demod
+ * (rtl_fm.c:759-824) on its block of bins per callback block, then the demod thread's gate (rtl_fm.c:927-940); one configuration for the bank:
+ *   power squelch (-l): sr = rms over the block's 2 * windows int16 (I and Q); sr < squelch_level: squelch_hits++ and the block's bins are
+ *     zeroed (fm_demod then sees zeros and leaves pre_r/pre_j = 0), else squelch_hits = 0.  The demodulator runs behind it.
+ *   mode: fm_demod / am_demod / usb_demod / lsb_demod / raw_demod (rtl_fm.c:584-665).  Only fm_demod moves pre_r/pre_j.  raw returns from
+ *     full_demod at once: de-emphasis and low_pass_real are skipped, a channel's row is its bins as int16 (I, Q) pairs and *windows_out is
+ *     the row length in int16 (2 per window).
+ *   gate: active = squelch_level && squelch_hits > conseq_squelch.  Active and !squelch_zero: squelch_hits = conseq_squelch + 1 and the
+ *     block is "dropped" -- still written to the row (rx_fm would not output it; rxgpu_chan_squelch_report says which).  Active and
+ *     squelch_zero: the block's final samples (behind low_pass_real when that is on) are zeros.
+ *   squelch_hits is a per-channel carry, 11 after rxgpu_chan_create (demod_init, rtl_fm.c:1091).  With mode != FM or a squelch the bank
+ *   stores every bin and the demodulator reads them back: the fused -A fast kernel keeps only a few. */
 typedef struct rxgpu_chan_params {
 	int bin_e;               /* window length 2^bin_e complex samples (1..15) */
 	int first_bin;           /* channel c = FFT bin (first_bin + c) mod N */
@@ -277,6 +290,12 @@ typedef struct rxgpu_chan_params {
 	 * rounded by FIX_MPY, rtl_power.c:256-262), then low_pass (rtl_fm.c:351-371) at downsample N; everything behind it as above.  The
 	 * same channels in another fixed-point rounding, at ~50 times the arithmetic: windows of 2^3 .. 2^12 samples. */
 	int nco;
+	int mode;                /* RXGPU_MODE_FM (0, default) / AM / USB / LSB / RAW: mode_demod per channel (rtl_fm.c:584-665) */
+	int output_scale;        /* am / usb / lsb multiplier (rtl_fm.c:625, 637, 648); 0 is taken as 1; ignored by fm and raw.  The library does
+	                          * not derive it: with nco = 1 rx_fm's formula (rtl_fm.c:988-992, downsample = N) has its literal meaning */
+	int squelch_level;       /* -l: full_demod's power squelch per channel and callback block (rtl_fm.c:781-790); 0 = off, < 0 refused */
+	int conseq_squelch;      /* -t: the demod thread's gate (rtl_fm.c:928-940), >= 0 */
+	int squelch_zero;        /* 0: a gated block is "dropped" (rx_fm does not output it); 1: its output is written as zeros (-t < 0) */
 } rxgpu_chan_params;
 
 typedef struct rxgpu_chan rxgpu_chan;
@@ -306,6 +325,15 @@ int rxgpu_chan_run_async(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, si
 int rxgpu_chan_wait(rxgpu_chan *s, size_t *windows_out);
 /* undecided libm samples the host settled in the runs the last rxgpu_chan_run / rxgpu_chan_wait retired */
 long rxgpu_chan_host_fixups(const rxgpu_chan *s);
+/* hits: n_channels squelch_hits (rtl_fm.c:145); like the other carries they refer to retired runs only */
+int rxgpu_chan_set_squelch_carry(rxgpu_chan *s, const int *hits);
+int rxgpu_chan_get_squelch_carry(rxgpu_chan *s, int *hits);
+/* of the runs the last rxgpu_chan_run / rxgpu_chan_wait retired -- one run, or with runs in flight the (at most two) runs the wait retired; the
+ * runs an rxgpu_chan_run_async retires on its own are not kept -- in block order (n_blocks: their blocks together, else RXGPU_EINVAL):
+ * sr[c * n_blocks + b] = full_demod's `sr` (rtl_fm.c:781; 0 with the squelch off), gate[c * n_blocks + b] = 0 written, 1 dropped, 2 zeroed.
+ * With the squelch on a run may hold at most max_blocks callback blocks (the verdicts are kept per block), even when shorter blocks than
+ * block_len would fit its windows: RXGPU_ECAPACITY otherwise. */
+int rxgpu_chan_squelch_report(rxgpu_chan *s, int *sr, uint8_t *gate, size_t n_blocks);
 
 /* --------------------------------------------------------- rx_power: drop-in */
 

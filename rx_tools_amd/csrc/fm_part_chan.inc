@@ -279,6 +279,196 @@ __global__ void k_ch_demod(const uint32_t *__restrict__ chan_lp, u64 total_windo
 	}
 }
 
+// ---- full_demod's power squelch and other demodulators per channel, the demod thread's gate (rxgpu_chan_params.mode .. squelch_zero).
+// They work on the dense bins ([channel][window], every window stored): the fused -A fast kernel keeps too few of them.
+
+// rtl_fm.c:781-790 with rms() 739-757 (step 1, over I and Q) on every (channel, callback block) segment of wpb bins: one thread per segment
+// (a wave per segment of 64 bins spent its time in the reduction: 216 us per 1 GiB capture), k_fm_squelch's int64 sums and double expression.
+// A quiet segment is zeroed in place: k_ch_demod's neighbour read at a block seam and the host's libm fix-ups (they re-read chan_lp) then see
+// what fm_demod sees in the reference.  below / sr_out: [channel][block].  VEC: wpb and total_windows multiples of 4, 16-byte pieces
+__device__ __forceinline__ void ch_sq_acc(uint32_t w, i64 &t, u64 &p)
+{
+	const int i = lo16(w), q = hi16(w);
+	t += i + q;
+	p += (u64)((unsigned)(i * i) + (unsigned)(q * q));          // <= 2^31: exact in 32 bits unsigned
+}
+// rms() (rtl_fm.c:739-757) from the block's sums in k_fm_squelch's double expression; true: below the level
+__device__ __forceinline__ bool ch_sq_verdict(i64 t, i64 p, u64 wpb, int level, int &sr)
+{
+	const int len = (int)(2 * wpb);
+	const double dc = (double)t / (double)len;              // (double)(t*step)/(double)len, step == 1
+	const double lhs = (double)(t * 2) * dc;
+	const double rhs = dc * dc * (double)len;
+	const double v = ((double)p - (lhs - rhs)) / (double)len;
+	sr = v >= 0.0 ? (int)isqrt_floor(v) : 0;
+	return sr < level;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ch_squelch(uint32_t *__restrict__ chan_lp, u64 total_windows, u64 wpb, u64 n_blocks, int n_channels, int level,
+                                                    uint8_t *__restrict__ below, int *__restrict__ sr_out)
+{
+	const u64 seg = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (seg >= (u64)n_channels * n_blocks)
+		return;
+	const u64 c = seg / n_blocks, b = seg - c * n_blocks;
+	uint32_t *lp = chan_lp + c * total_windows + b * wpb;
+	i64 t = 0;
+	u64 pu = 0;
+	if (VEC) {
+#pragma unroll 4
+		for (u64 m = 0; m < wpb; m += 4) {
+			const uint4 w = *reinterpret_cast<const uint4 *>(lp + m);
+			ch_sq_acc(w.x, t, pu); ch_sq_acc(w.y, t, pu); ch_sq_acc(w.z, t, pu); ch_sq_acc(w.w, t, pu);
+		}
+	} else {
+		for (u64 m = 0; m < wpb; m++)
+			ch_sq_acc(lp[m], t, pu);
+	}
+	int sr;
+	const bool quiet = ch_sq_verdict(t, (i64)pu, wpb, level, sr);
+	below[seg] = quiet ? 1 : 0;
+	sr_out[seg] = sr;
+	if (quiet) {
+		if (VEC)
+			for (u64 m = 0; m < wpb; m += 4)
+				*reinterpret_cast<uint4 *>(lp + m) = make_uint4(0u, 0u, 0u, 0u);
+		else
+			for (u64 m = 0; m < wpb; m++)
+				lp[m] = 0;
+	}
+}
+
+// The same for long blocks (wpb >= CH_SQ_WAVE_MIN windows: few channels, many windows per block -- a thread per segment would walk hundreds of KB
+// alone): one wave per segment, lanes strided over it, the int64 sums reduced across the wave
+#define CH_SQ_WAVE_MIN 512
+__global__ __launch_bounds__(256) void k_ch_squelch_wave(uint32_t *__restrict__ chan_lp, u64 total_windows, u64 wpb, u64 n_blocks, int n_channels,
+                                                         int level, uint8_t *__restrict__ below, int *__restrict__ sr_out)
+{
+	const u64 seg = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const unsigned lane = threadIdx.x & 63u;
+	if (seg >= (u64)n_channels * n_blocks)                   // wave-uniform
+		return;
+	const u64 c = seg / n_blocks, b = seg - c * n_blocks;
+	uint32_t *lp = chan_lp + c * total_windows + b * wpb;
+	i64 t = 0;
+	u64 pu = 0;
+	for (u64 m = lane; m < wpb; m += 64)
+		ch_sq_acc(lp[m], t, pu);
+	i64 p = (i64)pu;
+	for (int off = 32; off; off >>= 1) { t += __shfl_down(t, off); p += __shfl_down(p, off); }
+	t = __shfl(t, 0);
+	p = __shfl(p, 0);
+	int sr;
+	const bool quiet = ch_sq_verdict(t, p, wpb, level, sr);
+	if (lane == 0) {
+		below[seg] = quiet ? 1 : 0;
+		sr_out[seg] = sr;
+	}
+	if (quiet)
+		for (u64 m = lane; m < wpb; m += 64)
+			lp[m] = 0;
+}
+
+// am_demod / usb_demod / lsb_demod / raw_demod (rtl_fm.c:617-665) on the dense bins, grid (windows, channel): no 64-bit division per sample;
+// k_fm_simple_demod's arithmetic; raw: the bin as two int16 (rows of 2 * total_windows).  fm_demod's carry passes through: only fm_demod writes
+// pre_r / pre_j
+__global__ __launch_bounds__(256) void k_ch_simple_demod(const uint32_t *__restrict__ chan_lp, u64 total_windows, int mode, int output_scale,
+                                                         const int *__restrict__ pre_in, int *__restrict__ pre_out, int16_t *__restrict__ out, u64 out_stride)
+{
+	const u64 t = (u64)blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+	if (t >= total_windows)
+		return;
+	const uint32_t w = chan_lp[c * total_windows + t];
+	const int i = lo16(w), q = hi16(w);
+	int16_t *o = out + c * out_stride;
+	if (mode == RXK_LIT_RAW) {
+		o[2 * t] = (int16_t)i;
+		o[2 * t + 1] = (int16_t)q;
+	} else {
+		int v;
+		if (mode == RXK_LIT_AM) {
+			const int pw = (int)((unsigned)(i * i) + (unsigned)(q * q));    // may wrap at full scale, like the reference's int
+			v = pw < 0 ? 0 : (int)(short)isqrt_floor((double)pw);           // (int16_t)sqrt(NaN) is 0 on x86
+		} else {
+			v = (int)(short)(mode == RXK_LIT_USB ? i + q : i - q);
+		}
+		o[t] = (int16_t)(v * output_scale);
+	}
+	if (t == 0) {
+		pre_out[2 * c] = pre_in[2 * c];
+		pre_out[2 * c + 1] = pre_in[2 * c + 1];
+	}
+}
+
+// the demod thread's gate (rtl_fm.c:927-940) behind full_demod's count (781-790): one thread per channel walks the run's blocks in order --
+// squelch_hits from the verdicts, gate 0 written / 1 dropped (the hair trigger clamps the count) / 2 zeroed -- and leaves its count for the
+// next run on the device (hits_out: the next run's hits_in, like pre_out)
+__global__ void k_ch_gate(const uint8_t *__restrict__ below, u64 n_blocks, int n_channels, int conseq, int zero, const int *__restrict__ hits_in,
+                          int *__restrict__ hits_out, uint8_t *__restrict__ gate)
+{
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= n_channels)
+		return;
+	const uint8_t *bl = below + (u64)c * n_blocks;
+	uint8_t *g = gate + (u64)c * n_blocks;
+	int hits = hits_in[c];
+	// sixteen verdicts per load where the rows allow it, the next sixteen requested before these are walked (a byte per step waited for
+	// every load: 101 us for 2048 blocks)
+	const bool vec = (n_blocks & 15u) == 0 && (((size_t)bl | (size_t)g) & 15u) == 0;
+	const u64 nv = vec ? n_blocks : 0;
+	uint4 nxt = nv ? *reinterpret_cast<const uint4 *>(bl) : make_uint4(0u, 0u, 0u, 0u);
+	for (u64 b0 = 0; b0 < nv; b0 += 16) {
+		const uint4 cur = nxt;
+		if (b0 + 16 < nv)
+			nxt = *reinterpret_cast<const uint4 *>(bl + b0 + 16);
+		const uint32_t in[4] = {cur.x, cur.y, cur.z, cur.w};
+		uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+		for (int k = 0; k < 16; k++) {
+			hits = ((in[k >> 2] >> (8 * (k & 3))) & 0xffu) ? (int)((unsigned)hits + 1u) : 0;
+			uint32_t v = 0;
+			if (hits > conseq) {
+				if (zero)
+					v = 2;
+				else {
+					hits = conseq + 1;                      // hair trigger
+					v = 1;
+				}
+			}
+			o[k >> 2] |= v << (8 * (k & 3));
+		}
+		*reinterpret_cast<uint4 *>(g + b0) = make_uint4(o[0], o[1], o[2], o[3]);
+	}
+	for (u64 b = nv; b < n_blocks; b++) {
+		hits = bl[b] ? (int)((unsigned)hits + 1u) : 0;
+		uint8_t v = 0;
+		if (hits > conseq) {
+			if (zero)
+				v = 2;
+			else {
+				hits = conseq + 1;
+				v = 1;
+			}
+		}
+		g[b] = v;
+	}
+	hits_out[c] = hits;
+}
+
+// squelch_zero behind the audio stages: output j of a channel belongs to the block of the sample that emitted it -- with low_pass_real
+// (slow > 0) input sample lpr_end(j) - 1 (the phase p0 in front of the run is the same in every channel), else sample j
+__global__ void k_ch_gate_zero(int16_t *__restrict__ out, u64 out_stride, u64 J, u64 wpb, u64 n_blocks, int fast, int slow, u64 p0,
+                               const uint8_t *__restrict__ gate)
+{
+	const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+	if (j >= J)
+		return;
+	const u64 i = slow > 0 ? lpr_end(j, (u64)fast, (u64)slow, p0) - 1 : j;
+	const u64 b = i / wpb;
+	if (b < n_blocks && gate[c * n_blocks + b] == 2)
+		out[c * out_stride + j] = 0;
+}
+
 
 // Per-channel audio stages of the channeliser: deemph_filter (rtl_fm.c:667-682) and low_pass_real (389-409) on every
 // channel's demodulated stream, each channel with its own carried state like a demod_state of its own (rtl_fm.c:189

@@ -858,6 +858,52 @@ extern "C" int rxk_ch_demod(void *stream, const uint32_t *chan_lp, u64 total_win
 	LAUNCH_RET();
 }
 
+extern "C" int rxk_ch_squelch(void *stream, uint32_t *chan_lp, u64 total_windows, u64 wpb, int n_channels, int level, uint8_t *below, int *sr_out)
+{
+	const u64 n_blocks = total_windows / wpb, segs = (u64)n_channels * n_blocks;
+	if (!segs)
+		return 0;
+	if (wpb >= CH_SQ_WAVE_MIN) {
+		hipLaunchKernelGGL(k_ch_squelch_wave, dim3((unsigned)((segs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, chan_lp, total_windows, wpb, n_blocks,
+		                   n_channels, level, below, sr_out);
+		LAUNCH_RET();
+	}
+	const dim3 grid((unsigned)((segs + 255) / 256));
+	if (wpb % 4 == 0 && total_windows % 4 == 0)
+		hipLaunchKernelGGL(k_ch_squelch<true>, grid, dim3(256), 0, (hipStream_t)stream, chan_lp, total_windows, wpb, n_blocks, n_channels, level, below, sr_out);
+	else
+		hipLaunchKernelGGL(k_ch_squelch<false>, grid, dim3(256), 0, (hipStream_t)stream, chan_lp, total_windows, wpb, n_blocks, n_channels, level, below, sr_out);
+	LAUNCH_RET();
+}
+
+extern "C" int rxk_ch_simple_demod(void *stream, const uint32_t *chan_lp, u64 total_windows, int n_channels, int mode, int output_scale,
+                                   const int *pre_in, int *pre_out, int16_t *out, u64 out_stride)
+{
+	if (!total_windows || !n_channels)
+		return 0;
+	hipLaunchKernelGGL(k_ch_simple_demod, dim3((unsigned)((total_windows + 255) / 256), (unsigned)n_channels), dim3(256), 0, (hipStream_t)stream, chan_lp,
+	                   total_windows, mode, output_scale, pre_in, pre_out, out, out_stride);
+	LAUNCH_RET();
+}
+
+extern "C" int rxk_ch_gate(void *stream, const uint8_t *below, u64 n_blocks, int n_channels, int conseq, int zero, const int *hits_in, int *hits_out,
+                           uint8_t *gate)
+{
+	hipLaunchKernelGGL(k_ch_gate, dim3((unsigned)((n_channels + 63) / 64)), dim3(64), 0, (hipStream_t)stream, below, n_blocks, n_channels, conseq, zero,
+	                   hits_in, hits_out, gate);
+	LAUNCH_RET();
+}
+
+extern "C" int rxk_ch_gate_zero(void *stream, int16_t *out, u64 out_stride, u64 J, u64 wpb, u64 n_blocks, int n_channels, int fast, int slow, u64 p0,
+                                const uint8_t *gate)
+{
+	if (!J)
+		return 0;
+	hipLaunchKernelGGL(k_ch_gate_zero, dim3((unsigned)((J + 255) / 256), (unsigned)n_channels), dim3(256), 0, (hipStream_t)stream, out, out_stride, J,
+	                   wpb, n_blocks, fast, slow, p0, gate);
+	LAUNCH_RET();
+}
+
 // deemph_filter (rtl_fm.c:667-682) + low_pass_real (389-409) on ONE short row (the drop-in's single blocks: a thousand samples behind ds = 118),
 // k_ch_audio's scheme with the row in LDS and the chunk length cut loose from the warm-up: k_ch_audio walks global memory sample by sample
 // (46 us for 1 110 samples: every step of every chain waits for its load) and gives each thread a chunk of at least `warm` samples (ten threads

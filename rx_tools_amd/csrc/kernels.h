@@ -263,6 +263,19 @@ int rxk_ch_nco(void *stream, const int16_t *iq, unsigned long long total_windows
 int rxk_ch_demod(void *stream, const uint32_t *chan_lp, unsigned long long total_windows, unsigned long long wpb, int n_channels,
                  int custom_atan, const int *pre_in, int *pre_out, int16_t *out, unsigned long long out_stride,
                  rxk_fm_dev *dev, unsigned long long *flag_list, int sparse);
+/* full_demod's power squelch per (channel, callback block) of the DENSE chan_lp (rtl_fm.c:781-790): below / sr_out [channel][block],
+ * a quiet block's bins zeroed in place */
+int rxk_ch_squelch(void *stream, uint32_t *chan_lp, unsigned long long total_windows, unsigned long long wpb, int n_channels, int level,
+                   uint8_t *below, int *sr_out);
+/* am / usb / lsb / raw (mode: RXK_LIT_*) from the dense chan_lp into the rows (raw: 2 int16 per window); pre_out = pre_in */
+int rxk_ch_simple_demod(void *stream, const uint32_t *chan_lp, unsigned long long total_windows, int n_channels, int mode, int output_scale,
+                        const int *pre_in, int *pre_out, int16_t *out, unsigned long long out_stride);
+/* the demod thread's gate (rtl_fm.c:927-940) per channel over the run's blocks: squelch_hits in -> out, gate [channel][block] 0 / 1 dropped / 2 zeroed */
+int rxk_ch_gate(void *stream, const uint8_t *below, unsigned long long n_blocks, int n_channels, int conseq, int zero, const int *hits_in,
+                int *hits_out, uint8_t *gate);
+/* zero the outputs of gate-2 blocks in J samples per channel; slow > 0: behind low_pass_real fast -> slow from phase p0 */
+int rxk_ch_gate_zero(void *stream, int16_t *out, unsigned long long out_stride, unsigned long long J, unsigned long long wpb,
+                     unsigned long long n_blocks, int n_channels, int fast, int slow, unsigned long long p0, const uint8_t *gate);
 
 /* per-channel deemph_filter + low_pass_real on the channeliser's [channel][window] output (one workgroup per channel);
  * audio_in/out: {avg, now_lpr, prev_lpr_index} per channel; y_rows: scratch rows when slow > 0.  warm: samples that bring any two

@@ -33,19 +33,29 @@ struct rxgpu_chan {
 		int *pre_in_host, *pre_out_host;   /* pinned copies: carries in (a channel's first window re-evaluated on the host), carries out */
 		int16_t *rows;               /* where the run's demodulated samples went */
 		size_t rstride;
-		unsigned long long total;
+		unsigned long long total, n_blocks;
 		int fused;
+		/* squelch_level != 0: verdicts [channel][block] (device), sr / gate [channel][block] and the squelch_hits out (device, pinned copies) */
+		uint8_t *below, *gate_dev, *gate_host;
+		int *sr_dev, *sr_host, *hits_out_dev, *hits_out_host;
 		hipEvent_t done;
 	} run[2];
 	unsigned long long seq;
-	int chained;                     /* the previous enqueued run's pre_out_dev holds the carries (else pre_host does) */
+	int chained;                     /* the previous enqueued run's pre_out_dev (hits_out_dev) holds the carries (else pre_host, hits_host do) */
 	unsigned long long *flag_host;
-	size_t last_windows;
+	size_t last_windows, max_blocks;
 	long fixups, fixups_pending;
+	int *hits_up, *hits_host;        /* squelch_hits per channel: uploaded (a run not chained to one before it) / as of the last retired run */
+	/* rxgpu_chan_squelch_report: the runs the last drain retired (at most two, older first), read from their slots' pinned sr / gate copies --
+	 * fixed storage, nothing grows with the number of runs.  A slot's copies change only when a run is enqueued into it, which makes a run live
+	 * (the report is refused then) and empties this record */
+	int rep_slot[2], rep_runs;
+	unsigned long long rep_blocks[2];
 };
 
 static int chan_slots_alloc(rxgpu_chan *s, size_t nc)
 {
+	const size_t nb = s->p.squelch_level ? nc * s->max_blocks : 0;
 	for (int k = 0; k < 2; k++) {
 		struct chan_slot *r = &s->run[k];
 		if (hipMalloc((void **)&r->dev, sizeof(rxk_fm_dev)) != hipSuccess ||
@@ -56,6 +66,11 @@ static int chan_slots_alloc(rxgpu_chan *s, size_t nc)
 		    hipHostMalloc((void **)&r->pre_in_host, nc * 8, 0) != hipSuccess ||
 		    hipHostMalloc((void **)&r->pre_out_host, nc * 8, 0) != hipSuccess ||
 		    hipEventCreateWithFlags(&r->done, hipEventDisableTiming) != hipSuccess)
+			return RXGPU_ENOMEM;
+		if (nb && (hipMalloc((void **)&r->below, nb) != hipSuccess || hipMalloc((void **)&r->gate_dev, nb) != hipSuccess ||
+		           hipHostMalloc((void **)&r->gate_host, nb, 0) != hipSuccess || hipMalloc((void **)&r->sr_dev, nb * 4) != hipSuccess ||
+		           hipHostMalloc((void **)&r->sr_host, nb * 4, 0) != hipSuccess || hipMalloc((void **)&r->hits_out_dev, nc * 4) != hipSuccess ||
+		           hipHostMalloc((void **)&r->hits_out_host, nc * 4, 0) != hipSuccess))
 			return RXGPU_ENOMEM;
 	}
 	return RXGPU_OK;
@@ -84,6 +99,14 @@ int rxgpu_chan_create(rxgpu_chan **out, const rxgpu_chan_params *p, size_t max_b
 		return rxgpu_fail(RXGPU_EINVAL, "nco %d is neither 0 (bins of fix_fft) nor 1 (NCO -> low_pass)", p->nco);
 	if (p->nco && (p->bin_e < 3 || p->bin_e > 12))
 		return rxgpu_fail(RXGPU_EUNSUPPORTED, "NCO mode: windows of 2^3 .. 2^12 samples (window and table are staged in LDS)");
+	if (p->mode < RXGPU_MODE_FM || p->mode > RXGPU_MODE_RAW)
+		return rxgpu_fail(RXGPU_EINVAL, "mode %d outside 0..4 (RXGPU_MODE_FM .. RXGPU_MODE_RAW)", p->mode);
+	if (p->squelch_level < 0)
+		return rxgpu_fail(RXGPU_EINVAL, "squelch_level %d < 0", p->squelch_level);
+	if (p->conseq_squelch < 0)
+		return rxgpu_fail(RXGPU_EINVAL, "conseq_squelch %d < 0", p->conseq_squelch);
+	if (p->squelch_zero != 0 && p->squelch_zero != 1)
+		return rxgpu_fail(RXGPU_EINVAL, "squelch_zero %d is neither 0 nor 1", p->squelch_zero);
 	if ((rc = rxgpu_ensure_init()) != RXGPU_OK)
 		return rc;
 	rxgpu_knobs_reload();                            /* the object keeps the kernel variants chosen now */
@@ -91,6 +114,9 @@ int rxgpu_chan_create(rxgpu_chan **out, const rxgpu_chan_params *p, size_t max_b
 	if (!s)
 		return rxgpu_fail(RXGPU_ENOMEM, "out of host memory");
 	s->p = *p;
+	if (!s->p.output_scale)
+		s->p.output_scale = 1;
+	s->max_blocks = max_blocks;
 	s->max_windows = max_blocks * (block_len / 2 / n);
 	uint32_t *tw = malloc((n + 2) * 4);
 	if (!tw) { free(s); return rxgpu_fail(RXGPU_ENOMEM, "out of host memory"); }
@@ -112,6 +138,7 @@ int rxgpu_chan_create(rxgpu_chan **out, const rxgpu_chan_params *p, size_t max_b
 	    chan_slots_alloc(s, nc) != RXGPU_OK ||
 	    hipHostMalloc((void **)&s->flag_host, RXK_FLAG_CAP * 8, 0) != hipSuccess ||
 	    hipHostMalloc((void **)&s->pre_host, nc * 8, 0) != hipSuccess ||
+	    hipMalloc((void **)&s->hits_up, nc * 4) != hipSuccess || hipHostMalloc((void **)&s->hits_host, nc * 4, 0) != hipSuccess ||
 	    hipMemcpy(s->twiddle_dev, tw, (n + 2) * 4, hipMemcpyHostToDevice) != hipSuccess) {
 		free(tw);
 		rxgpu_chan_destroy(s);
@@ -134,6 +161,8 @@ int rxgpu_chan_create(rxgpu_chan **out, const rxgpu_chan_params *p, size_t max_b
 	}
 	memset(s->pre_host, 0, nc * 8);
 	memset(s->audio_host, 0, nc * 12);
+	for (size_t c = 0; c < nc; c++)
+		s->hits_host[c] = 11;                            /* demod_init, rtl_fm.c:1091 */
 	*out = s;
 	return RXGPU_OK;
 }
@@ -150,11 +179,17 @@ void rxgpu_chan_destroy(rxgpu_chan *s)
 		if (r->dev_host) hipHostFree(r->dev_host);
 		if (r->pre_in_host) hipHostFree(r->pre_in_host);
 		if (r->pre_out_host) hipHostFree(r->pre_out_host);
+		hipFree(r->below); hipFree(r->gate_dev); hipFree(r->sr_dev); hipFree(r->hits_out_dev);
+		if (r->gate_host) hipHostFree(r->gate_host);
+		if (r->sr_host) hipHostFree(r->sr_host);
+		if (r->hits_out_host) hipHostFree(r->hits_out_host);
 	}
 	hipFree(s->audio_dev[0]); hipFree(s->audio_dev[1]); hipFree(s->audio_y); hipFree(s->audio_ctab); hipFree(s->audio_seg);
 	if (s->audio_host) hipHostFree(s->audio_host);
 	if (s->flag_host) hipHostFree(s->flag_host);
 	if (s->pre_host) hipHostFree(s->pre_host);
+	hipFree(s->hits_up);
+	if (s->hits_host) hipHostFree(s->hits_host);
 	free(s);
 }
 
@@ -201,6 +236,57 @@ int rxgpu_chan_get_audio_carry(rxgpu_chan *s, int *audio)
 /* -1 while runs are in flight: the count is settled when a run is retired (rxgpu_chan_wait), like the carries */
 long rxgpu_chan_host_fixups(const rxgpu_chan *s) { return !s ? 0 : (s->run[0].live || s->run[1].live) ? -1 : s->fixups; }
 
+int rxgpu_chan_set_squelch_carry(rxgpu_chan *s, const int *hits)
+{
+	if (!s || !hits)
+		return rxgpu_fail(RXGPU_EINVAL, "null argument");
+	if (s->run[0].live || s->run[1].live)
+		return rxgpu_fail(RXGPU_EINVAL, "rxgpu_chan_set_squelch_carry with runs in flight: rxgpu_chan_wait first");
+	memcpy(s->hits_host, hits, (size_t)s->p.n_channels * 4);
+	s->chained = 0;                                        /* the next run takes pre_host and hits_host (both current: nothing in flight) */
+	return RXGPU_OK;
+}
+
+int rxgpu_chan_get_squelch_carry(rxgpu_chan *s, int *hits)
+{
+	if (!s || !hits)
+		return rxgpu_fail(RXGPU_EINVAL, "null argument");
+	if (s->run[0].live || s->run[1].live)
+		return rxgpu_fail(RXGPU_EINVAL, "rxgpu_chan_get_squelch_carry with runs in flight: rxgpu_chan_wait first");
+	memcpy(hits, s->hits_host, (size_t)s->p.n_channels * 4);
+	return RXGPU_OK;
+}
+
+int rxgpu_chan_squelch_report(rxgpu_chan *s, int *sr, uint8_t *gate, size_t n_blocks)
+{
+	if (!s || !sr || !gate)
+		return rxgpu_fail(RXGPU_EINVAL, "null argument");
+	if (s->run[0].live || s->run[1].live)
+		return rxgpu_fail(RXGPU_EINVAL, "rxgpu_chan_squelch_report with runs in flight: rxgpu_chan_wait first");
+	unsigned long long blocks = 0;
+	for (int k = 0; k < s->rep_runs; k++)
+		blocks += s->rep_blocks[k];
+	if (n_blocks != blocks)
+		return rxgpu_fail(RXGPU_EINVAL, "the runs the last run / wait retired hold %llu blocks, not %zu", blocks, n_blocks);
+	const size_t nc = (size_t)s->p.n_channels;
+	if (!s->p.squelch_level) {                             /* squelch off: full_demod's sr stays 0, every block is written */
+		memset(sr, 0, nc * n_blocks * 4);
+		memset(gate, 0, nc * n_blocks);
+		return RXGPU_OK;
+	}
+	size_t b0 = 0;
+	for (int k = 0; k < s->rep_runs; k++) {
+		const struct chan_slot *r = &s->run[s->rep_slot[k]];
+		const size_t nb = (size_t)s->rep_blocks[k];
+		for (size_t c = 0; c < nc; c++) {
+			memcpy(sr + c * n_blocks + b0, r->sr_host + c * nb, nb * 4);
+			memcpy(gate + c * n_blocks + b0, r->gate_host + c * nb, nb);
+		}
+		b0 += nb;
+	}
+	return RXGPU_OK;
+}
+
 /* samples until trajectories from the two ends of the int16 range are fewer than `a` apart (then at most one adjacent pair
  * of candidates merges per sample, which is what the mask tracking relies on): the gap g shrinks by at least floor(g / a) per
  * sample (k_fm_deemph_scan's argument).  a <= 64, so the candidates also fit the 64-bit mask. */
@@ -229,18 +315,27 @@ static int chan_enqueue(rxgpu_chan *s, int k, const int16_t *d_iq, unsigned long
 	hipStream_t st = rxgpu_hip_stream();
 	struct chan_slot *r = &s->run[k];
 	const size_t nc = (size_t)s->p.n_channels;
-	const int *pre_in;
+	const int *pre_in, *hits_in = NULL;
+	const int squelch = s->p.squelch_level != 0, fm = s->p.mode == RXGPU_MODE_FM;
+	s->rep_runs = 0;                                          /* the slot's sr / gate copies are about to change */
 	memset(r->dev_host, 0, sizeof(*r->dev_host));
 	RX_HIP(hipMemsetAsync(r->dev, 0, sizeof(rxk_fm_dev), st));
 	if (s->chained) {
 		pre_in = s->run[k ^ 1].pre_out_dev;
+		hits_in = s->run[k ^ 1].hits_out_dev;
 	} else {
 		RX_HIP(hipMemcpyAsync(s->pre_up, s->pre_host, nc * 8, hipMemcpyHostToDevice, st));
 		pre_in = s->pre_up;
+		if (squelch) {
+			RX_HIP(hipMemcpyAsync(s->hits_up, s->hits_host, nc * 4, hipMemcpyHostToDevice, st));
+			hits_in = s->hits_up;
+		}
 	}
 	RX_HIP(hipMemcpyAsync(r->pre_in_host, pre_in, nc * 8, hipMemcpyDeviceToHost, st));
-	/* -A fast with whole groups of windows per block: fm_demod runs inside the FFT kernel for all but each group's first window */
-	const int fused = s->p.nco ? 0 : rxk_ch_fused_ok(s->p.bin_e, wpb, s->p.custom_atan, s->p.n_channels);
+	/* -A fast with whole groups of windows per block: fm_demod runs inside the FFT kernel for all but each group's first window.  Another
+	 * demodulator or a squelch in front of fm_demod needs every bin: the dense form */
+	const int fused = (s->p.nco || !fm || squelch) ? 0 : rxk_ch_fused_ok(s->p.bin_e, wpb, s->p.custom_atan, s->p.n_channels);
+	const unsigned long long n_blocks = total / wpb;
 	rxgpu_prof_begin("ch_fft");
 	if (s->p.nco)                                         /* SURVEY 8(f)2's literal definition: NCO -> low_pass at downsample N, per channel */
 		RX_K(rxk_ch_nco(st, d_iq, total, s->p.bin_e, s->nco_tw_dev, s->p.first_bin, s->p.n_channels, r->chan_lp));
@@ -249,13 +344,25 @@ static int chan_enqueue(rxgpu_chan *s, int k, const int16_t *d_iq, unsigned long
 		                r->pre_out_dev));
 	rxgpu_prof_end("ch_fft");
 	rxgpu_prof_begin("ch_demod");
-	RX_K(rxk_ch_demod(st, r->chan_lp, total, wpb, s->p.n_channels, s->p.custom_atan, pre_in, r->pre_out_dev, rows, rstride,
-	                  r->dev, r->flag_list, fused));
+	if (squelch)                                          /* full_demod: the squelch in front of the demodulator (rtl_fm.c:781-790) */
+		RX_K(rxk_ch_squelch(st, r->chan_lp, total, wpb, s->p.n_channels, s->p.squelch_level, r->below, r->sr_dev));
+	if (fm)
+		RX_K(rxk_ch_demod(st, r->chan_lp, total, wpb, s->p.n_channels, s->p.custom_atan, pre_in, r->pre_out_dev, rows, rstride,
+		                  r->dev, r->flag_list, fused));
+	else
+		RX_K(rxk_ch_simple_demod(st, r->chan_lp, total, s->p.n_channels, s->p.mode, s->p.output_scale, pre_in, r->pre_out_dev, rows, rstride));
+	if (squelch)                                          /* the demod thread behind it (rtl_fm.c:927-940) */
+		RX_K(rxk_ch_gate(st, r->below, n_blocks, s->p.n_channels, s->p.conseq_squelch, s->p.squelch_zero, hits_in, r->hits_out_dev, r->gate_dev));
 	rxgpu_prof_end("ch_demod");
 	RX_HIP(hipMemcpyAsync(r->dev_host, r->dev, sizeof(rxk_fm_dev), hipMemcpyDeviceToHost, st));
 	RX_HIP(hipMemcpyAsync(r->pre_out_host, r->pre_out_dev, nc * 8, hipMemcpyDeviceToHost, st));
+	if (squelch) {
+		RX_HIP(hipMemcpyAsync(r->sr_host, r->sr_dev, nc * n_blocks * 4, hipMemcpyDeviceToHost, st));
+		RX_HIP(hipMemcpyAsync(r->gate_host, r->gate_dev, nc * n_blocks, hipMemcpyDeviceToHost, st));
+		RX_HIP(hipMemcpyAsync(r->hits_out_host, r->hits_out_dev, nc * 4, hipMemcpyDeviceToHost, st));
+	}
 	RX_HIP(hipEventRecord(r->done, st));
-	r->rows = rows; r->rstride = rstride; r->total = total; r->fused = fused;
+	r->rows = rows; r->rstride = rstride; r->total = total; r->fused = fused; r->n_blocks = n_blocks;
 	r->live = 1;
 	s->chained = 1;
 	return RXGPU_OK;
@@ -314,8 +421,11 @@ static int chan_check_run(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, s
 	const unsigned long long wpb = block_len / 2 / n, total = wpb * n_blocks;
 	if (total > s->max_windows)
 		return rxgpu_fail(RXGPU_ECAPACITY, "channeliser created for %zu windows, run asks %llu", s->max_windows, total);
-	if (out_stride < total)
-		return rxgpu_fail(RXGPU_ECAPACITY, "out_stride %zu shorter than %llu windows", out_stride, total);
+	if (s->p.squelch_level && n_blocks > s->max_blocks)    /* the verdicts are kept per block */
+		return rxgpu_fail(RXGPU_ECAPACITY, "channeliser with squelch created for %zu blocks, run asks %zu", s->max_blocks, n_blocks);
+	const unsigned long long row = s->p.mode == RXGPU_MODE_RAW ? 2 * total : total;     /* raw: (I, Q) int16 per window */
+	if (out_stride < row)
+		return rxgpu_fail(RXGPU_ECAPACITY, "out_stride %zu shorter than the %llu int16 of a row", out_stride, row);
 	*wpb_out = wpb; *total_out = total;
 	return RXGPU_OK;
 }
@@ -325,10 +435,20 @@ static int chan_drain(rxgpu_chan *s)
 {
 	int rc;
 	const int newest = (int)((s->seq + 1) & 1);              /* slot of run seq - 1 */
-	if ((rc = chan_retire(s, newest ^ 1)) != RXGPU_OK || (rc = chan_retire(s, newest)) != RXGPU_OK)
-		return rc;
-	if (s->seq && s->chained)
+	s->rep_runs = 0;                                          /* the report: the runs THIS drain retires, older first */
+	for (int k = newest ^ 1, i = 0; i < 2; i++, k ^= 1) {
+		if (!s->run[k].live)
+			continue;
+		if ((rc = chan_retire(s, k)) != RXGPU_OK)
+			return rc;
+		s->rep_slot[s->rep_runs] = k;
+		s->rep_blocks[s->rep_runs++] = s->run[k].n_blocks;
+	}
+	if (s->seq && s->chained) {
 		memcpy(s->pre_host, s->run[newest].pre_out_host, (size_t)s->p.n_channels * 8);
+		if (s->p.squelch_level)
+			memcpy(s->hits_host, s->run[newest].hits_out_host, (size_t)s->p.n_channels * 4);
+	}
 	s->fixups = s->fixups_pending;
 	s->fixups_pending = 0;
 	return RXGPU_OK;
@@ -340,7 +460,7 @@ int rxgpu_chan_run_async(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, si
 	unsigned long long wpb, total;
 	if ((rc = chan_check_run(s, d_iq, n_blocks, block_len, d_out, out_stride, &wpb, &total)) != RXGPU_OK)
 		return rc;
-	if (s->p.deemph || s->p.rate_out2 > 0)
+	if ((s->p.deemph || s->p.rate_out2 > 0) && s->p.mode != RXGPU_MODE_RAW)
 		/* the audio stages start from samples a host fix-up may still change: such a channeliser runs call by call */
 		return rxgpu_chan_run(s, d_iq, n_blocks, block_len, d_out, out_stride, &s->last_windows);
 	const int k = (int)(s->seq & 1);
@@ -349,7 +469,7 @@ int rxgpu_chan_run_async(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, si
 	if ((rc = chan_enqueue(s, k, d_iq, total, wpb, d_out, out_stride)) != RXGPU_OK)
 		return rc;
 	s->seq++;
-	s->last_windows = (size_t)total;
+	s->last_windows = (size_t)(s->p.mode == RXGPU_MODE_RAW ? 2 * total : total);
 	return RXGPU_OK;
 }
 
@@ -378,7 +498,8 @@ int rxgpu_chan_run(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, size_t b
 		return rc;
 	/* per-channel audio stages: which form serves this run is known before anything is launched -- the (segment, channel) grid reads the
 	 * demodulated rows from a buffer of its own (audio_y) and writes the audio to d_out, k_ch_audio works on d_out in place */
-	const int audio_on = s->p.deemph || s->p.rate_out2 > 0;
+	/* raw_demod returns from full_demod before the audio stages (rtl_fm.c:809-811): they are accepted and skipped */
+	const int audio_on = (s->p.deemph || s->p.rate_out2 > 0) && s->p.mode != RXGPU_MODE_RAW;
 	int serial = s->p.deemph && (s->p.deemph_a < 2 || s->p.deemph_a > 64);
 	for (size_t c = 0; c < nc && s->p.deemph && !serial; c++)
 		if (s->audio_host[3 * c] < -32768 || s->audio_host[3 * c] > 32767)
@@ -394,12 +515,12 @@ int rxgpu_chan_run(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, size_t b
 	s->seq++;
 	if ((rc = chan_drain(s)) != RXGPU_OK)
 		return rc;
-	unsigned long long per_channel = total;
+	unsigned long long per_channel = s->p.mode == RXGPU_MODE_RAW ? 2 * total : total;
 	if (audio_on) {
 		/* per-channel audio stages on the finished (and, where needed, host-corrected) demodulated rows */
 		unsigned long long J = total;
+		const int p0 = s->audio_host[2];                      /* the phase advances alike in every channel */
 		if (s->p.rate_out2 > 0) {
-			const int p0 = s->audio_host[2];                  /* the phase advances alike in every channel */
 			for (size_t c = 0; c < nc; c++)
 				if (s->audio_host[3 * c + 2] != p0 || p0 < 0 || p0 >= s->p.rate_out)
 					return rxgpu_fail(RXGPU_EINVAL, "prev_lpr_index must be the same in [0, rate_out) for every channel");
@@ -415,6 +536,12 @@ int rxgpu_chan_run(rxgpu_chan *s, const int16_t *d_iq, size_t n_blocks, size_t b
 			RX_K(rxk_ch_audio(st, d_out, out_stride, total, s->p.n_channels, s->p.deemph, s->p.deemph_a, warm, serial, s->p.rate_out,
 			                  s->p.rate_out2 > 0 ? s->p.rate_out2 : 0, J, s->audio_dev[0], s->audio_dev[1], s->audio_y, s->max_windows));
 		rxgpu_prof_end("ch_audio");
+		/* -t < 0 (squelch_zero): a gated block's final samples are zeros (rtl_fm.c:935-936), after the audio stages, which ran on its
+		 * demodulated samples like the reference's do.  Without audio stages a gated block is a quiet one: its bins are zero, and so is every
+		 * demodulated sample (never a libm flag, which needs a nonzero value) -- nothing to do there */
+		if (s->p.squelch_level && s->p.squelch_zero)
+			RX_K(rxk_ch_gate_zero(st, d_out, out_stride, J, wpb, total / wpb, s->p.n_channels, s->p.rate_out, s->p.rate_out2 > 0 ? s->p.rate_out2 : 0,
+			                      (unsigned long long)p0, s->run[k].gate_dev));
 		RX_HIP(hipMemcpyAsync(s->audio_host, s->audio_dev[1], nc * 12, hipMemcpyDeviceToHost, st));
 		RX_HIP(hipStreamSynchronize(st));
 		rxgpu_prof_collect();

@@ -118,9 +118,14 @@ class FmStream:
         return lib().rxgpu_fm_stream_host_fixups(self._h)
 
 
+# enum RXGPU_MODE_* of include/rxgpu.h (ChanParams.mode, FmParams.mode)
+RXGPU_MODE_FM, RXGPU_MODE_AM, RXGPU_MODE_USB, RXGPU_MODE_LSB, RXGPU_MODE_RAW = range(5)
+
+
 class ChanParams(C.Structure):
-    """struct rxgpu_chan_params (channeliser extension, include/rxgpu.h)"""
-    _fields_ = [(n, C.c_int) for n in ("bin_e", "first_bin", "n_channels", "custom_atan", "deemph", "deemph_a", "rate_out", "rate_out2", "nco")]
+    """struct rxgpu_chan_params (channeliser extension, include/rxgpu.h); the fields behind `nco` default to 0 = FM without squelch"""
+    _fields_ = [(n, C.c_int) for n in ("bin_e", "first_bin", "n_channels", "custom_atan", "deemph", "deemph_a", "rate_out", "rate_out2", "nco",
+                                       "mode", "output_scale", "squelch_level", "conseq_squelch", "squelch_zero")]
 
 
 class Channeliser:
@@ -179,3 +184,24 @@ class Channeliser:
     @property
     def host_fixups(self):
         return lib().rxgpu_chan_host_fixups(self._h)
+
+    def set_squelch_carry(self, hits):
+        import numpy as np
+        h = np.ascontiguousarray(hits, dtype=np.int32)
+        check(lib().rxgpu_chan_set_squelch_carry(self._h, h.ctypes.data))
+
+    def get_squelch_carry(self):
+        """squelch_hits per channel after the retired runs"""
+        import numpy as np
+        h = np.zeros(self.params.n_channels, dtype=np.int32)
+        check(lib().rxgpu_chan_get_squelch_carry(self._h, h.ctypes.data))
+        return h
+
+    def squelch_report(self, n_blocks):
+        """(sr int32 [n_channels, n_blocks], gate uint8 [n_channels, n_blocks]) of the runs the last run() / wait() retired:
+        full_demod's rms per block, and 0 written / 1 dropped / 2 zeroed"""
+        import numpy as np
+        sr = np.zeros((self.params.n_channels, n_blocks), dtype=np.int32)
+        gate = np.zeros((self.params.n_channels, n_blocks), dtype=np.uint8)
+        check(lib().rxgpu_chan_squelch_report(self._h, sr.ctypes.data, gate.ctypes.data, n_blocks))
+        return sr, gate
